@@ -209,6 +209,29 @@ int ufm_debug_set_upsample_variant(int tiled);
 int ufm_warp_bilinear(const void* target, int tgt_dtype, int Ht, int Wt, const float* flow, int H, int W,
                       const float* mask, int mask_mode, float fill, float* out, void* stream);
 
+/* Sparse matches with forward-backward consistency (ufm_amd/matching.py::extract_matches).  Per image b:
+ * F = flow_st[b] fp32 [2][Hs][Ws], Cs = covis_s[b] [Hs][Ws], G = flow_ts[b] [2][Ht][Wt], Ct = covis_t[b] [Ht][Wt].
+ * Source pixel p = (x, y) maps to q = p + F(p); G and Ct are sampled at q bilinearly on pixel indices
+ * (x0 = min(floor(qx), Wt-2), 0 when Wt == 1, wx = qx - x0; the same for y;
+ *  v = (1-wy)((1-wx) v00 + wx v01) + wy((1-wx) v10 + wx v11)); cycle error e = |q + G(q) - p|.
+ * p is valid when q lies in [0, Wt-1] x [0, Ht-1], every value read is finite, Cs(p) >= covis_threshold,
+ * Ct(q) >= covis_threshold and e <= cycle_threshold; score s = Cs(p) Ct(q) / (1 + e).
+ * The source is tiled into cell x cell blocks from (0, 0); a cell's candidate is its valid pixel of largest s (ties: lowest
+ * y*Ws + x).  The K candidates of largest s (ties: lowest index) are returned in that order.
+ *   ufm_match_ws_bytes:    bytes of the workspace `ws` both calls share (negative UFM_ERR_* on bad sizes).
+ *   ufm_match_consistency: fills the per-cell keys in ws; score / err (optional, fp32 [B][Hs][Ws]) receive s (0 where
+ *                          invalid) and e (+inf where q is outside the box).  Thresholds must be >= 0.
+ *   ufm_match_topk:        after ufm_match_consistency on the same ws: matches fp32 [B][K][4] = (xs, ys, xt, yt) with
+ *                          (xt, yt) = q, 16-byte aligned; scores fp32 [B][K]; counts int32 [B] = min(K, #candidates).
+ *                          Rows at or past counts[b]: matches NaN, scores 0.  1 <= K <= 8192, cell >= 1, Hs*Ws < 2^31.
+ * Deterministic and batch-invariant (integer max on packed keys, no float atomics). */
+int64_t ufm_match_ws_bytes(int B, int Hs, int Ws, int cell, int K);
+int ufm_match_consistency(const float* flow_st, const float* covis_s, const float* flow_ts, const float* covis_t, int B, int Hs,
+                          int Ws, int Ht, int Wt, int cell, float covis_threshold, float cycle_threshold, void* ws,
+                          int64_t ws_bytes, float* score, float* err, void* stream);
+int ufm_match_topk(const float* flow_st, int B, int Hs, int Ws, int cell, int K, void* ws, int64_t ws_bytes, float* matches,
+                   float* scores, int* counts, void* stream);
+
 /* =====================================================================================
  * LayerNorm over the channel dim, eps inside the sqrt ([U] Block.norm1/norm2, encoder .norm,
  * info-sharing .norm; nn.LayerNorm(eps=1e-6)).  x: fp32 [*, D] rows of stride ldx.

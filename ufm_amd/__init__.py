@@ -9,17 +9,20 @@ Drop-in surface (same names as ``uniflowmatch``): ``UniFlowMatch``, ``UniFlowMat
 from .base import (
     UFMClassificationRefinementOutput,
     UFMFlowFieldOutput,
+    UFMMatchesOutput,
     UFMMaskFieldOutput,
     UFMOutputInterface,
     UniFlowMatchModelsBase,
 )
 from .configs import make_config, ufm_base_config, ufm_refine_config, ufm_tiny_config
 from .graph import GraphedPredictor
+from .matching import extract_matches
 from .ufm import UniFlowMatch, UniFlowMatchClassificationRefinement, UniFlowMatchConfidence
 
 __all__ = [
     "UFMClassificationRefinementOutput",
     "UFMFlowFieldOutput",
+    "UFMMatchesOutput",
     "UFMMaskFieldOutput",
     "UFMOutputInterface",
     "UniFlowMatchModelsBase",
@@ -27,6 +30,7 @@ __all__ = [
     "UniFlowMatchClassificationRefinement",
     "UniFlowMatchConfidence",
     "GraphedPredictor",
+    "extract_matches",
     "make_config",
     "ufm_base_config",
     "ufm_refine_config",

@@ -46,6 +46,16 @@ class UFMClassificationRefinementOutput:
 
 
 @dataclass
+class UFMMatchesOutput:
+    """Sparse matches (ufm_amd.matching.extract_matches / predict_matches): matches (B, K, 4) fp32 [xs, ys, xt, yt],
+    scores (B, K) fp32, counts (B,) int32; rows at or past counts[b] hold NaN matches and 0 scores."""
+
+    matches: torch.Tensor
+    scores: torch.Tensor
+    counts: torch.Tensor
+
+
+@dataclass
 class UFMOutputInterface:
     flow: Optional[UFMFlowFieldOutput] = None
     classification_refinement: Optional[UFMClassificationRefinementOutput] = None
@@ -155,6 +165,39 @@ class UniFlowMatchModelsBase(torch.nn.Module):
         else:
             raise ValueError("source_image and target_image must be of type torch.float32 or torch.uint8")
         return self._predict(source_image, target_image, layout, scale3, shift3, (hs, ws), (ht, wt))
+
+    def predict_matches(
+        self,
+        source_image: torch.Tensor,
+        target_image: torch.Tensor,
+        data_norm_type: Optional[str] = None,
+        num_matches: int = 5000,
+        cell: int = 8,
+        covisibility_threshold: float = 0.5,
+        cycle_threshold_px: float = 1.0,
+    ) -> "UFMMatchesOutput":
+        """Sparse, forward-backward consistent matches source -> target (ufm_amd.matching.extract_matches on both
+        directions of predict_correspondences_batched; same inputs).  Equal-sized images run as one batch of 2B pairs
+        (source ++ target against target ++ source), others as two calls.  Needs a model with a covisibility head."""
+        from .matching import extract_matches
+
+        if source_image.dim() == 3:
+            source_image, target_image = source_image.unsqueeze(0), target_image.unsqueeze(0)
+        B = source_image.shape[0]
+        if source_image.shape == target_image.shape:
+            both = self.predict_correspondences_batched(torch.cat([source_image, target_image]), torch.cat([target_image, source_image]), data_norm_type)
+            if both.covisibility is None:
+                raise ValueError(f"{type(self).__name__} has no covisibility output: predict_matches needs one")
+            flow, covis = both.flow.flow_output, both.covisibility.mask
+            fwd_flow, fwd_covis, bwd_flow, bwd_covis = flow[:B], covis[:B], flow[B:], covis[B:]
+        else:
+            fwd = self.predict_correspondences_batched(source_image, target_image, data_norm_type)
+            if fwd.covisibility is None:
+                raise ValueError(f"{type(self).__name__} has no covisibility output: predict_matches needs one")
+            bwd = self.predict_correspondences_batched(target_image, source_image, data_norm_type)
+            fwd_flow, fwd_covis, bwd_flow, bwd_covis = fwd.flow.flow_output, fwd.covisibility.mask, bwd.flow.flow_output, bwd.covisibility.mask
+        return extract_matches(fwd_flow, fwd_covis, bwd_flow, bwd_covis, num_matches=num_matches, cell=cell,
+                               covisibility_threshold=covisibility_threshold, cycle_threshold_px=cycle_threshold_px)
 
     def _predict(self, src, tgt, layout, scale3, shift3, src_hw, tgt_hw) -> UFMOutputInterface:
         """base.py:236-334: resize -> forward -> un-map, all on device."""

@@ -20,6 +20,7 @@ import sys
 from pathlib import Path
 
 ARTEFACTS = ("flow_visualization.png", "covisibility_mask.png", "warped_source.png")
+MATCHES = "matches.npz"  # `infer --matches N`: matches (n, 4) [xs, ys, xt, yt] and scores (n,), n <= N
 HUB_IDS = {"base": "infinity1096/UFM-Base", "refine": "infinity1096/UFM-Refine"}  # cli.py:109-111
 MODEL_FLAG = dict(choices=sorted(HUB_IDS), default="base", help="Model variant to use (default: base)")
 
@@ -41,6 +42,8 @@ def build_parser() -> argparse.ArgumentParser:
     pair.add_argument("--weights", help="local save_pretrained directory or .ckpt file (default: the reference's Hub id)")
     pair.add_argument("--random-init", action="store_true", help="seeded random weights instead of a checkpoint")
     pair.add_argument("--numerics", choices=("fast", "precise", "parity"), default="fast")
+    pair.add_argument("--matches", type=int, metavar="N",
+                      help="also write matches.npz: up to N forward-backward consistent matches (xs, ys, xt, yt) and their scores")
 
     commands.add_parser("test", help="Test installation")
     return root
@@ -68,7 +71,7 @@ def _fail(message: str) -> None:
     sys.exit(1)
 
 
-def _infer(args) -> Path:
+def _infer(args):
     import numpy as np
     import torch
 
@@ -96,13 +99,26 @@ def _infer(args) -> Path:
     images_out = (viz.flow_to_color(flow_hw2), (covis * 255).astype(np.uint8), blended)
     for name, image in zip(ARTEFACTS, images_out):
         viz.save_png(out_dir / name, image)
-    return out_dir
+    if getattr(args, "matches", None) is None:
+        return out_dir, None
+    # the target -> source direction, then the consistency check against the forward prediction already at hand
+    from ufm_amd.matching import extract_matches
+
+    with torch.no_grad():
+        backward = model.predict_correspondences_batched(
+            source_image=torch.from_numpy(target).to("cuda"), target_image=torch.from_numpy(source).to("cuda")
+        )
+    found = extract_matches(prediction.flow.flow_output, prediction.covisibility.mask, backward.flow.flow_output,
+                            backward.covisibility.mask, num_matches=args.matches)
+    n = int(found.counts[0].item())
+    np.savez(out_dir / MATCHES, matches=found.matches[0, :n].cpu().numpy(), scores=found.scores[0, :n].cpu().numpy())
+    return out_dir, n
 
 
 def run_inference(args) -> None:
     """cli.py:85-156."""
     try:
-        out_dir = _infer(args)
+        out_dir, n_matches = _infer(args)
     except ImportError as exc:
         _fail(f"Error importing dependencies: {exc}\nPlease ensure all dependencies are installed")
     except SystemExit:
@@ -112,6 +128,8 @@ def run_inference(args) -> None:
     print(f"Results saved to: {out_dir}")
     for name in ARTEFACTS:
         print(f"- {name}")
+    if n_matches is not None:
+        print(f"- {MATCHES} ({n_matches} matches)")
 
 
 def test_installation() -> None:

@@ -84,9 +84,11 @@ SIGNATURES = {
     "ufm_pixel_shuffle_planar": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "ufm_cast_f32_to_bf16": [_vp, _vp, _i64, _vp],
     "ufm_add_f32": [_vp, _vp, _vp, _i64, _vp],
+    "ufm_match_consistency": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp],
+    "ufm_match_topk": [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp],
 }
 SIGNATURES["ufm_conv_x3_register_interleaved_weights"] = [_vp, _vp]
-PLAIN = {"ufm_conv_x3_splitk_ws_bytes": (C.c_longlong, [C.c_int] * 10), "ufm_group_norm_ws_floats": (C.c_int, [C.c_int, C.c_int, C.c_int]), "ufm_abi_version": (C.c_int, []), "ufm_last_error": (C.c_char_p, []), "ufm_built_arch": (C.c_char_p, [])}
+PLAIN = {"ufm_conv_x3_splitk_ws_bytes": (C.c_longlong, [C.c_int] * 10), "ufm_group_norm_ws_floats": (C.c_int, [C.c_int, C.c_int, C.c_int]), "ufm_match_ws_bytes": (C.c_int64, [C.c_int] * 5), "ufm_abi_version": (C.c_int, []), "ufm_last_error": (C.c_char_p, []), "ufm_built_arch": (C.c_char_p, [])}
 
 
 def lib() -> C.CDLL:
@@ -507,3 +509,25 @@ def cast_bf16(x, out):
 
 def add_f32(a, b, out):
     _check(lib().ufm_add_f32(_p(a), _p(b), _p(out), a.numel(), _stream()), "ufm_add_f32")
+
+
+def match_ws_bytes(B, Hs, Ws, cell, K) -> int:
+    n = int(lib().ufm_match_ws_bytes(B, Hs, Ws, cell, K))
+    if n < 0:
+        raise RuntimeError(f"ufm_match_ws_bytes failed (rc={n}): {lib().ufm_last_error().decode()}")
+    return n
+
+
+def match_consistency(flow_st, covis_s, flow_ts, covis_t, cell, covis_threshold, cycle_threshold, ws, score=None, err=None):
+    """flow_st (B, 2, Hs, Ws), covis_s (B, Hs, Ws), flow_ts (B, 2, Ht, Wt), covis_t (B, Ht, Wt) fp32; ws: uint8 workspace of
+    match_ws_bytes(); score / err: optional fp32 (B, Hs, Ws) dense maps."""
+    B, _, Hs, Ws = flow_st.shape
+    Ht, Wt = flow_ts.shape[2:]
+    _check(lib().ufm_match_consistency(_p(flow_st), _p(covis_s), _p(flow_ts), _p(covis_t), B, Hs, Ws, Ht, Wt, cell, float(covis_threshold), float(cycle_threshold),
+                                       _p(ws), ws.numel() * ws.element_size(), _p(score), _p(err), _stream()), "ufm_match_consistency")
+
+
+def match_topk(flow_st, cell, K, ws, matches, scores, counts):
+    """After match_consistency on the same ws: matches (B, K, 4) fp32, scores (B, K) fp32, counts (B,) int32."""
+    B, _, Hs, Ws = flow_st.shape
+    _check(lib().ufm_match_topk(_p(flow_st), B, Hs, Ws, cell, K, _p(ws), ws.numel() * ws.element_size(), _p(matches), _p(scores), _p(counts), _stream()), "ufm_match_topk")
